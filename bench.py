@@ -50,6 +50,34 @@ CONFIGS = {
     "train8_f32": dict(batch=8, frames=300, objective="acoustic", dtype="f32", model_set="A", train=True),
 }
 PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}   # dense MFMA peaks, MI355X_MICROARCH.md chip-level parameters
+DUMP_LIMIT = 64 << 20   # bytes that --dump-outputs writes at most
+DUMP_SEED = 20200905
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: writes every array of ``outputs`` (name -> tensor / array, rows first) as DIR/<name>.npy, float32 (float64
+    stays float64).  When all of them together exceed DUMP_LIMIT, every array keeps the same share of its rows, drawn with a
+    fixed seed, and DIR/<name>_rows.npy lists the rows kept: two builds write the same sample.  Returns the names written."""
+    import numpy as np
+    arrs = {}
+    for name, v in outputs.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT:
+        share = 0.95 * DUMP_LIMIT / total   # room for the row lists
+        for name in list(arrs):
+            a = arrs[name]
+            if a.ndim == 0 or a.shape[0] < 2:
+                continue
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=max(1, int(a.shape[0] * share)), replace=False))
+            arrs[name] = np.ascontiguousarray(a[rows])
+            arrs[name + "_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    progress(f"outputs of the last timed step written to {dirname} ({sum(a.nbytes for a in arrs.values()) / 2**20:.1f} MiB)")
+    return sorted(arrs)
 
 
 def cpu_baseline(wl_args, objective, seconds_budget=25.0, full=False):
@@ -149,6 +177,11 @@ def bench_train(args, cfg):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     eng.synchronize()
+    dumped = None
+    if args.dump_outputs:   # the last step's loss and the parameters it left (what pred_model.load_state_dict receives)
+        outs = {"loss": losses[-1].reshape(1)}
+        outs.update({f"pred.{k}": v for k, v in eng.get_weights("pred").items()})
+        dumped = dump_outputs(args.dump_outputs, outs)
     H, I, M = 720, 30, 60
     per_frame = 4 * H * (I + H) + H * M
     flops = 2 * B * T * per_frame * 3                      # forward + backward-data + weight gradients
@@ -167,6 +200,8 @@ def bench_train(args, cfg):
            "roofline": {"bound": "mfma", "kernel": ("lstm_bwd16_rs_sweep_kernel" if B <= 128 else "lstm_bwd_rs_stream_kernel") if cfg["dtype"] == "bf16" else "lstm_bwd_sweep_f32_kernel",
                         "achieved": fl / (ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
                         "frac": fl / (ms * 1e-3) / 1e12 / peak, "traffic": None, "avg_launch_us": ms * 1e3}}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_train(cfg)
     print(json.dumps(out), flush=True)
@@ -201,6 +236,8 @@ def plumbing_only(args, cfg):
         elapsed = float(tmax.item())
         outs = [torch.empty_like(cp) for _ in range(world)]
         dist.all_gather(outs, cp)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cp": torch.cat(outs)})
     if rank == 0:
         print(json.dumps({"plumbing_only": True, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": elapsed / max(1, args.steps) * 1e3, "scaling": "weak",
@@ -251,6 +288,9 @@ def main():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="multi-rank plumbing without an engine (rendezvous, barrier, max-over-ranks timing, all_gather of a CP-shaped "
                          "tensor, rank-0 JSON): what tests/test_host.py runs on a machine without a GPU; prints \"plumbing_only\": true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (final CP trajectories and loss rows; training "
+                         "configs: loss and parameters) as DIR/<name>.npy, float32, at most 64 MB (a fixed sample of rows beyond that)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -344,6 +384,9 @@ def main():
         gather_ms = (time.perf_counter() - tg) * 1e3
     eng.synchronize()   # surfaces device-side failures (bounded in-kernel waits) -- outside the timed region
     finite = bool(torch.isfinite(loss).all().item() and torch.isfinite(cp).all().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the final CP trajectories (all ranks') and the last step's loss rows [B, 8]
+        dumped = dump_outputs(args.dump_outputs, {"cp": torch.cat([o.cpu() for o in outs]) if world > 1 else cp, "loss": loss[-1]})
 
     if rank == 0:
         progress(f"timed region done: {elapsed / args.steps * 1e3:.3f} ms/step")
@@ -457,6 +500,8 @@ def main():
         }
         if gather_ms is not None:
             out["final_cp_all_gather_ms"] = gather_ms
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         progress("kernel timing done; cpu baseline")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, cfg["objective"], full=args.cpu_full)

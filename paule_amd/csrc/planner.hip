@@ -268,6 +268,9 @@ struct pl_handle {
     struct WfSeg { hipGraphNode_t before, last; int dep1, dep2; };   // chain neighbours of a (layer, chunk) segment; true dependencies
     struct WfRegion { std::vector<WfSeg> segs; std::vector<int> finals; };
     std::vector<WfRegion> wf_regions;
+    bool graph_branches = true; // build_graph rewrites the wavefront's edges into parallel branches.  Off where the runtime has fewer than 4
+                                // hardware queues (GPU_MAX_HW_QUEUES): the first launch of a branched exec crashes there,
+                                // so the graph stays the captured chain
     bool capturing = false;
     size_t wf_stream_next = 0;  // cursor into the device's pool of layer streams: every wavefront region of an iteration takes its own
                                 // (HIP's capture does not survive a stream that is forked, joined and forked again with others)
@@ -2049,6 +2052,8 @@ int build_graph(pl_handle* h) {
     hipError_t e = hipStreamEndCapture(h->cap_stream, &h->graph);
     DBG_G("end capture done");
     if (e != hipSuccess) return fail(PL_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    // too few hardware queues for a branched exec: the captured chain is a valid order of the same nodes (same bits, no overlap)
+    if (!h->graph_branches) h->wf_regions.clear();
     if (!h->wf_regions.empty()) {
         // the capture is one chain; give the wavefront regions their real dependencies: segment (layer, chunk) waits for
         // (layer below / above, same chunk) and (same layer, previous chunk) only, the node after a region for all its final segments
@@ -2381,6 +2386,10 @@ int pl_create(const pl_config* cfg, pl_handle** out) {
         if (const char* z = std::getenv("PAULE_HIP_PIPE_SPREAD")) h->pipe_spread = std::atoi(z) != 0;
 #endif
         if (const char* z = std::getenv("PAULE_HIP_WAVEFRONT")) h->wavefront = std::atoi(z);
+        if (const char* z = std::getenv("GPU_MAX_HW_QUEUES")) {   // the runtime's own setting (default 4: a branched exec runs on 4 queues)
+            const int q = std::atoi(z);
+            if (q > 0 && q < 4) h->graph_branches = false;
+        }
 #ifdef PL_EXPERIMENTS   // A/B-only switch (its measured winner is the fixed default of the shipped library: DESIGN.md 4.1c)
         if (const char* z = std::getenv("PAULE_HIP_WF_DIRS")) h->wf_dirs = std::atoi(z);
 #endif

@@ -582,31 +582,61 @@ def test_fused_forward_is_bit_identical(HipPlanner, monkeypatch, shape):
     assert (e["1"].losses[-1, :, 0] < e["1"].losses[0, :, 0]).all()
 
 
-@pytest.mark.parametrize("shape", [dict(B=144, T=61, H=720, gpp="2"), dict(B=200, T=33, H=96, gpp="4"), dict(B=300, T=20, H=96, gpp="2", set_b=True)])
-def test_fused_forward_in_passes_is_bit_identical(HipPlanner, monkeypatch, shape):
-    """Round 4: batches of more 32-row groups than the forward launch's roles hold at once (cfg4's 2048 rows on one GPU: 64 groups) run
-    the launch in PASSES -- the role table of one chip-load, every role walking its sets pass after pass (lstm_fused.hip:
-    fused_fwd_kernel, FusedArgs::gpp).  Forced here at small batches (PAULE_HIP_FUSED_GPP: 5 groups in passes of 2, 7 in passes of 4,
-    ragged last groups, a last pass with fewer sets than roles have; the stacked two-width predictor): every forward stash, the pooled
-    mel, losses and the plan equal the per-layer path's bit for bit."""
+_PASSES_CORE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "paule_amd", "csrc", "libpaule_hip_passes.so")
+
+
+def _fused_forward_in_passes_check(shape):
+    """Body of test_fused_forward_in_passes_is_bit_identical, run in a child process whose library is the -DFUSED_PASSES=1 core (the
+    loader binds ONE core per process)."""
+    from paule_amd.engine import HipPlanner
     B, T, H = shape["B"], shape["T"], shape["H"]
-    if "FUSED_PASSES=1" not in os.environ.get("PAULE_HIP_BUILD_OPTIONS", ""):
-        pytest.skip("the pass loop is a build option since round 5 (make EXTRA=-DFUSED_PASSES=1; set PAULE_HIP_BUILD_OPTIONS=FUSED_PASSES=1 to run this test)")
     if shape.get("set_b"):
         wl = synthetic.make_workload(B, T, "B")
         bufs = [f"pred.{k}{l}" for l in range(4) for k in "hcG"] + ["mel", "mel_tm", "emb.h0", "emb.c0", "emb.G0"]
     else:
         wl = synthetic.make_workload(B, T, None, pred=dict(num_lstm_layers=1, hidden_size=H), emb=dict(num_lstm_layers=2, hidden_size=H))
         bufs = FWD_BUFFERS
-    monkeypatch.setenv("PAULE_HIP_DEBUG", "stop_after_fwd")
-    e = _fused_pair(HipPlanner, monkeypatch, wl, B, T, ("0", "1"), 1, False, dict(PAULE_HIP_FUSED_GPP=shape["gpp"]))
-    for name in bufs:
-        np.testing.assert_array_equal(_n(e["1"].debug_read(name)), _n(e["0"].debug_read(name)), err_msg=name)
-    monkeypatch.delenv("PAULE_HIP_DEBUG")
-    e = _fused_pair(HipPlanner, monkeypatch, wl, B, T, ("0", "1"), 3, True, dict(PAULE_HIP_FUSED_GPP=shape["gpp"]))
-    np.testing.assert_array_equal(e["1"].losses, e["0"].losses)
-    np.testing.assert_array_equal(_n(e["1"].get_cp()), _n(e["0"].get_cp()))
-    monkeypatch.delenv("PAULE_HIP_FUSED_GPP")
+    with pytest.MonkeyPatch.context() as monkeypatch:
+        # the pass loop really is compiled in and switched on: the role table is planned for gpp groups, not for all of them
+        # (otherwise the comparison below would be one of the single-pass launch with itself)
+        single = _fused_pair(HipPlanner, monkeypatch, wl, B, T, ("1",), 0, False)["1"]
+        plan_single = single.plan_info()
+        single.close()
+        monkeypatch.setenv("PAULE_HIP_DEBUG", "stop_after_fwd")
+        e = _fused_pair(HipPlanner, monkeypatch, wl, B, T, ("0", "1"), 1, False, dict(PAULE_HIP_FUSED_GPP=shape["gpp"]))
+        assert e["1"].plan_info() != plan_single, (e["1"].plan_info(), plan_single)
+        for name in bufs:
+            np.testing.assert_array_equal(_n(e["1"].debug_read(name)), _n(e["0"].debug_read(name)), err_msg=name)
+        monkeypatch.delenv("PAULE_HIP_DEBUG")
+        e = _fused_pair(HipPlanner, monkeypatch, wl, B, T, ("0", "1"), 3, True, dict(PAULE_HIP_FUSED_GPP=shape["gpp"]))
+        np.testing.assert_array_equal(e["1"].losses, e["0"].losses)
+        np.testing.assert_array_equal(_n(e["1"].get_cp()), _n(e["0"].get_cp()))
+        monkeypatch.delenv("PAULE_HIP_FUSED_GPP")
+
+
+@pytest.mark.parametrize("shape", [dict(B=144, T=61, H=720, gpp="2"), dict(B=200, T=33, H=96, gpp="4"), dict(B=300, T=20, H=96, gpp="2", set_b=True)])
+def test_fused_forward_in_passes_is_bit_identical(shape):
+    """Round 4: batches of more 32-row groups than the forward launch's roles hold at once (cfg4's 2048 rows on one GPU: 64 groups) run
+    the launch in PASSES -- the role table of one chip-load, every role walking its sets pass after pass (lstm_fused.hip:
+    fused_fwd_kernel, FusedArgs::gpp).  Forced here at small batches (PAULE_HIP_FUSED_GPP: 5 groups in passes of 2, 7 in passes of 4,
+    ragged last groups, a last pass with fewer sets than roles have; the stacked two-width predictor): every forward stash, the pooled
+    mel, losses and the plan equal the per-layer path's bit for bit.  The pass loop is a build option since round 5: build() makes the
+    core with it (libpaule_hip_passes.so), and the comparison runs in a child process on that core."""
+    import json
+    import subprocess
+    import sys
+    assert os.path.exists(_PASSES_CORE), f"{_PASSES_CORE} is missing: build() makes it (make -C paule_amd/csrc passes)"
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import json, sys\n"
+            "sys.path[:0] = [sys.argv[1], sys.argv[2]]\n"
+            "import test_hip_parity as t\n"
+            "t._fused_forward_in_passes_check(json.loads(sys.argv[3]))\n"
+            "print('OK')\n")
+    env = {k: v for k, v in os.environ.items() if k not in ("PAULE_HIP_CORE", "PAULE_HIP_LIB") and not k.startswith("PAULE_HIP_FUSED")}
+    env["PAULE_HIP_LIB"] = _PASSES_CORE
+    out = subprocess.run([sys.executable, "-c", code, os.path.dirname(here), here, json.dumps(shape)], capture_output=True, text=True,
+                         timeout=600, env=env)
+    assert out.returncode == 0 and "OK" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
 
 
 @pytest.mark.parametrize("shape", [dict(B=256, T=300, H=720, graph=True), dict(B=144, T=61, H=720, graph=False),

@@ -470,6 +470,35 @@ def test_bench_launches_its_own_ranks():
     assert out["ms_per_step"] >= 0.02 * 1e3 / 2   # the slowest rank's time, not rank 0's
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files of what the run computed; beyond the 64 MB bound the same seeded sample of rows
+    in every run, with the rows kept listed beside it."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "rehearsal", "--plumbing-only", "--steps", "2",
+                        "--dump-outputs", str(tmp_path / "plumb")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    cp = np.load(tmp_path / "plumb" / "cp.npy")
+    assert cp.dtype == np.float32 and cp.shape == (8, 60, 30)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 16)
+    big = np.arange(1000 * 40, dtype=np.float64).reshape(1000, 40)
+    small_rows = torch.arange(1000 * 4, dtype=torch.float32).reshape(1000, 4)
+    for d in ("a", "b"):
+        names = bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small_rows})
+        assert names == ["big", "big_rows", "small", "small_rows"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 1 << 16
+    rows = np.load(tmp_path / "a" / "big_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big[rows]) and np.all(np.diff(rows) > 0)
+
+
 def test_planner_cache_is_keyed_by_architecture_and_lru(small):
     """the handle cache of Paule._get_planner -- keyed by the models' architecture (not by id(): a freed model's id can
     come back), least recently used out, bounded by bytes, and the handle published as `paule.planner` is never closed under the
